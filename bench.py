@@ -17,6 +17,13 @@ the GPU, spawns N rank processes with RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* set (127.0.0.1), relays rank 0's JSON line and exits non-zero if any
 rank fails.  The line reports the world size the process group saw and every
 rank's own rate.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N steps and prints the line.  `--full` adds the bounded CPU
+baselines (`cpu_baseline`, --cpu-seconds; ~40 s of host time) to the line.
+`--dump-outputs DIR` writes what the last timed step() returned (obs, reward,
+done) as DIR/<name>.npy: the same arguments give the same inputs and, the step
+being deterministic, the same arrays.
 """
 from __future__ import annotations
 
@@ -61,8 +68,13 @@ def parse(argv=None):
     ap.add_argument("--reward", default="bbpow_action")
     ap.add_argument("--coupling", default="auto", choices=["auto", "f32", "bf16x3"],
                     help="coupling arithmetic (kura.h KURA_COUPLING_*; auto = bf16x3 at every N)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baselines (--cpu-seconds)")
     ap.add_argument("--cpu-seconds", type=float, default=24.0,
-                    help="bounded CPU-baseline budget in seconds (0 = skip), split over its legs")
+                    help="--full: bounded CPU-baseline budget in seconds (0 = skip), split over its legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step() returned as DIR/<name>.npy (float32 / float64; "
+                         "rank r > 0 writes <name>.rank<r>.npy)")
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--reset-reps", type=int, default=1,
                     help="time this many resets of the same state (extra.reset_ms_warm: the fastest after the first)")
@@ -75,7 +87,33 @@ def parse(argv=None):
                     help="(CPU test of the --gpus N launcher) ranks only join the process group and report")
     ap.add_argument("--rank-timeout", type=float, default=1800.0,
                     help="launcher: seconds before the spawned ranks are killed")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: upper bound of one rank's files together
+
+
+def dump_outputs(path, outputs, rank=0, seed=0):
+    """Write {name: array} (one leading env axis each) as path/<name>.npy:
+    floats keep their width, everything else becomes float32 (exact for the
+    0/1 done flags).  A set above DUMP_MAX_BYTES is cut to the same seeded,
+    sorted sample of envs in every array, stored as env_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: np.ascontiguousarray(v, dtype=v.dtype if v.dtype in (np.float32, np.float64) else np.float32)
+            for k, v in outputs.items()}
+    B = next(iter(arrs.values())).shape[0]
+    per_env = sum(a.nbytes for a in arrs.values()) / B + 4   # + its env_index entry
+    keep = int((DUMP_MAX_BYTES - 256 * (len(arrs) + 1)) // per_env)   # 256 B cover each file's .npy header
+    if keep < B:
+        idx = np.sort(np.random.default_rng(seed).choice(B, size=max(keep, 1), replace=False))
+        arrs = {k: np.ascontiguousarray(a[idx]) for k, a in arrs.items()}
+        arrs["env_index"] = idx.astype(np.float32)
+    sfx = f".rank{rank}" if rank else ""
+    for k, a in arrs.items():
+        np.save(os.path.join(path, f"{k}{sfx}.npy"), a)
 
 
 def build_shard(args, rank):
@@ -426,9 +464,9 @@ def main(argv=None):
     if not args.share_device and local_rank >= torch.cuda.device_count():
         print(f"[bench] LOCAL_RANK={local_rank} but {torch.cuda.device_count()} visible GPU(s)", file=sys.stderr)
         sys.exit(2)
-    # CPU baseline first: the reference-op leg forks worker processes, which
-    # must happen before this process initialises the GPU
-    cpu = cpu_baseline(args) if (world == 1 and args.cpu_seconds > 0) else None
+    # CPU baseline (--full) first: the reference-op leg forks worker processes,
+    # which must happen before this process initialises the GPU
+    cpu = cpu_baseline(args) if (args.full and world == 1 and args.cpu_seconds > 0) else None
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     if world > 1:
@@ -484,12 +522,15 @@ def main(argv=None):
     t0 = time.perf_counter()
     for k in range(args.steps):
         ev[k][0].record(stream)
-        sim.step(acts[args.warmup + k])
+        ret = sim.step(acts[args.warmup + k])
         ev[k][1].record(stream)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in zip(("obs", "reward", "done"), ret)},
+                     rank, args.seed)
     kern_ms = [a.elapsed_time(b) for a, b in ev]
     st1 = sim.stats()
     steps_attempted = int(st1[5] - st0[5]) // args.steps   # per launch, averaged over the timed launches

@@ -62,6 +62,49 @@ def test_bench_modes_are_documented(flag):
     assert f'"{flag}"' in src
 
 
+def test_bench_full_and_dump_options():
+    """A plain run skips the CPU baselines (--full turns them on); --steps is
+    the number of timed steps, so it must be positive."""
+    bench = importlib.import_module("bench")
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d" and a.cpu_seconds > 0
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files named after the step's
+    outputs; above the size bound every array holds the same seeded sample of
+    envs, identical from run to run."""
+    import numpy as np
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(0)
+    B = 37
+    outs = {"obs": rng.standard_normal((B, 50)).astype(np.float32), "reward": rng.standard_normal(B),
+            "done": (rng.random(B) < 0.5).astype(np.uint8)}
+    bench.dump_outputs(str(tmp_path / "a"), outs, 0, 5)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["done", "obs", "reward"]
+    assert got["obs"].dtype == np.float32 and got["reward"].dtype == np.float64 and got["done"].dtype == np.float32
+    for k in outs:
+        assert np.array_equal(got[k], outs[k])
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), outs, 0, 5)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["done.npy", "env_index.npy", "obs.npy", "reward.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= 4096
+    idx = np.load(tmp_path / "b" / "env_index.npy").astype(int)
+    assert 0 < len(idx) < B and np.all(np.diff(idx) > 0)
+    for k in outs:
+        assert np.array_equal(np.load(tmp_path / "b" / f"{k}.npy"), outs[k][idx])
+        assert np.array_equal(np.load(tmp_path / "b" / f"{k}.npy"), np.load(tmp_path / "c" / f"{k}.npy"))
+    bench.dump_outputs(str(tmp_path / "a"), outs, 3, 5)
+    assert os.path.exists(tmp_path / "a" / "obs.rank3.npy")
+
+
 def test_rocprof_summary_backs_the_bench_roofline():
     """The bench line's roofline.traffic comes from the committed rocprofv3
     summary of the same workload, and that summary's traced kernel average

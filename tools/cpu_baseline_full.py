@@ -4,7 +4,7 @@ weak #8): env0 default params (N=512), a single env, 1000 steps after
 reset(), on the host's cores -- (i) one core, (ii) all cores with one env
 per process -- through oracle/ref_numpy.py, the reference's step() op
 sequence (fmod + direct N^2 sin coupling, env.py:252-256; Dopri5/PID/dense
-output; R1).  The bench's default cpu_baseline is a bounded sample of the
+output; R1).  The cpu_baseline of `bench.py --full` is a bounded sample of the
 same code (tens of seconds); this is the long form, run on the GPU box's
 host without touching the GPU:
 
