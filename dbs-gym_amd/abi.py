@@ -149,6 +149,9 @@ _SYMBOLS = {
     "kura_selftest_math": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "kura_selftest_gemm": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "kura_selftest_coupling": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),
+    "kura_selftest_alpha_reuse": (c_int, []),
+    "kura_alpha_reuse": (c_int, [c_void_p]),
+    "kura_alpha_reuse_detect": (c_int, [c_void_p, c_int]),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))

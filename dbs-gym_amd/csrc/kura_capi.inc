@@ -160,6 +160,7 @@ static void fill_params(KuraHandle* h) {
     p.alpha_sw = h->alpha_sw;
     p.alpha_dd = h->alpha_dd;
     p.alpha_dd_bytes = (unsigned)(h->alpha_dd_cap * sizeof(float));
+    p.alpha_reuse = 0;   // kura_set_coupling decides
     p.omega = h->omega;
     p.kn_env = h->kn_env;
     p.g_stim = h->g_stim;
@@ -242,6 +243,30 @@ static void split_alpha(const float* alpha, uint16_t* sp, int N) {
     const int NB = N / 16;
     for (int jt = 0; jt < N / 32; ++jt)
         for (int b = 0; b < NB; ++b) split_fragment(alpha, N, jt, b, sp + ((size_t)jt * NB + b) * 3 * 64 * 8);
+}
+
+// Does the pre-split N = 1024 image (split_alpha) have the shift structure
+// coupling_gemm_bf16x3_shift relies on?  Every fragment that form does not
+// load -- column tile jt with jt % 4 != 0, k-block b with b % 8 >= 2, 1152 of
+// 2048 -- must equal, byte for byte, the one it reuses: (jt - 1, b - 2).
+// Pure host code; decided from the data on every kura_set_coupling.
+static bool alpha_shift_reuse(const uint16_t* sp, int N) {
+    if (N != 1024) return false;
+    const int NB = N / 16;
+    const size_t FU16 = 3 * 64 * 8;   // uint16 per fragment
+    for (int jt = 0; jt < N / 32; ++jt)
+        for (int b = 0; b < NB; ++b) {
+            if (jt % 4 == 0 || b % 8 < 2) continue;
+            if (memcmp(sp + ((size_t)jt * NB + b) * FU16, sp + ((size_t)(jt - 1) * NB + (b - 2)) * FU16, FU16 * 2))
+                return false;
+        }
+    return true;
+}
+// KURA_ALPHA_REUSE=0 in the environment forces the general GEMM (tests, the
+// same-binary A/B); read on every call.
+static bool alpha_reuse_allowed() {
+    const char* e = getenv("KURA_ALPHA_REUSE");
+    return !(e && e[0] == '0' && e[1] == 0);
 }
 
 // alpha in the layout of the handle's coupling GEMM (floats of the image:
@@ -547,12 +572,18 @@ int kura_set_coupling(KuraHandle* h, const float* alpha) {
     if (!h || !alpha) return set_err(KURA_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(h->device));
     const int N = h->cfg.n_osc;
+    // a failed upload leaves the handle without a coupling (and without a
+    // dangling image pointer): set again only after every upload succeeded
+    h->have_coupling = false;
+    h->p.alpha_reuse = 0;
     const std::vector<float> sw = coupling_image(alpha, N, h->sp, h->tpw);
     if (sw.size() > h->alpha_cap) {   // the deduplicated image: sized to its distinct fragments
         HIP_TRY(hipDeviceSynchronize());   // no launch in flight reads the old image
-        HIP_TRY(hipFree(h->alpha_sw));
+        float* old = h->alpha_sw;
         h->alpha_sw = nullptr;
         h->alpha_cap = 0;
+        h->p.alpha_sw = nullptr;
+        HIP_TRY(hipFree(old));
         if (int rc = dalloc(&h->alpha_sw, sw.size())) return rc;
         h->alpha_cap = sw.size();
         h->p.alpha_sw = h->alpha_sw;
@@ -562,9 +593,12 @@ int kura_set_coupling(KuraHandle* h, const float* alpha) {
         const std::vector<float> dd = split_alpha_dedup(alpha, N);
         if (dd.size() > h->alpha_dd_cap) {
             HIP_TRY(hipDeviceSynchronize());
-            if (h->alpha_dd) HIP_TRY(hipFree(h->alpha_dd));
+            float* old = h->alpha_dd;
             h->alpha_dd = nullptr;
             h->alpha_dd_cap = 0;
+            h->p.alpha_dd = nullptr;
+            h->p.alpha_dd_bytes = 0;
+            if (old) HIP_TRY(hipFree(old));
             if (int rc = dalloc(&h->alpha_dd, dd.size())) return rc;
             h->alpha_dd_cap = dd.size();
             h->p.alpha_dd = h->alpha_dd;
@@ -572,8 +606,24 @@ int kura_set_coupling(KuraHandle* h, const float* alpha) {
         }
         HIP_TRY(hipMemcpy(h->alpha_dd, dd.data(), dd.size() * sizeof(float), hipMemcpyHostToDevice));
     }
+    // K1's BF16X3 step GEMM at N = 1024: the shift-reuse form where the data allow it
+    h->p.alpha_reuse = h->sp && !h->xl && alpha_reuse_allowed() &&
+                       alpha_shift_reuse(reinterpret_cast<const uint16_t*>(sw.data()), N);
     h->have_coupling = true;
     return KURA_OK;
+}
+
+int kura_alpha_reuse(KuraHandle* h) {
+    if (!h) return set_err(KURA_E_INVALID, "null handle");
+    return h->have_coupling && h->p.alpha_reuse ? 1 : 0;
+}
+
+int kura_alpha_reuse_detect(const float* alpha, int n_osc) {
+    if (!alpha) return set_err(KURA_E_INVALID, "null argument");
+    if (n_osc != 1024) return 0;
+    std::vector<uint16_t> sp((size_t)n_osc * n_osc * 3);
+    split_alpha(alpha, sp.data(), n_osc);
+    return alpha_shift_reuse(sp.data(), n_osc) ? 1 : 0;
 }
 
 int kura_set_env_params(KuraHandle* h, int env0, int n, const float* omega, const double* g_stim,
@@ -1073,6 +1123,9 @@ int kura_selftest_math(const float* x, const float* y, float* out, int n) {
     return rc;
 }
 
+static int g_selftest_reuse = 0;   // GEMM form of the last kura_selftest_coupling
+int kura_selftest_alpha_reuse(void) { return g_selftest_reuse; }
+
 int kura_selftest_coupling(const float* X /* 32*N */, const float* alpha /* N*N */, float* Y /* 32*N */, int N,
                            int coupling) {
     if (N != 256 && N != 512 && N != 1024) return set_err(KURA_E_UNSUPPORTED, "N=%d", N);
@@ -1080,6 +1133,9 @@ int kura_selftest_coupling(const float* X /* 32*N */, const float* alpha /* N*N 
         return set_err(KURA_E_INVALID, "coupling=%d", coupling);
     const bool sp = coupling != KURA_COUPLING_F32;   // AUTO = BF16X3 (at every N, kura_coupling_of)
     const std::vector<float> sw = coupling_image(alpha, N, sp, N / 256);
+    // the production dispatch (kura_set_coupling): the shift-reuse form where the data allow it
+    int reuse = sp && alpha_reuse_allowed() && alpha_shift_reuse(reinterpret_cast<const uint16_t*>(sw.data()), N);
+    g_selftest_reuse = reuse;
     float *dX = nullptr, *dA = nullptr, *dY = nullptr;
     int rc = dalloc(&dX, (size_t)32 * N);
     rc = rc ? rc : dalloc(&dA, sw.size());
@@ -1091,7 +1147,7 @@ int kura_selftest_coupling(const float* X /* 32*N */, const float* alpha /* N*N 
     if (!rc) {
         (void)hipMemcpy(dX, X, (size_t)32 * N * sizeof(float), hipMemcpyHostToDevice);
         (void)hipMemcpy(dA, sw.data(), sw.size() * sizeof(float), hipMemcpyHostToDevice);
-        void* argv[] = {(void*)&dX, (void*)&dA, (void*)&dY, (void*)&N};
+        void* argv[] = {(void*)&dX, (void*)&dA, (void*)&dY, (void*)&N, (void*)&reuse};
         hipError_t e = hipLaunchKernel(k, dim3(1), dim3(NTHREADS), argv, lds, 0);
         if (e == hipSuccess) e = hipDeviceSynchronize();
         if (e != hipSuccess) rc = set_err(KURA_E_HIP, "selftest_gemm: %s", hipGetErrorString(e));

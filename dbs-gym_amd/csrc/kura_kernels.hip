@@ -68,6 +68,7 @@ struct DevParams {
     const float* alpha_sw;  // B-fragment swizzled coupling
     const float* alpha_dd;  // BF16X3, N <= 1024: the deduplicated image too (the reset's GEMM, -DKURA_RESET_DEDUP)
     unsigned alpha_dd_bytes;  // its size (the GEMM's descriptor range)
+    int alpha_reuse;        // BF16X3, N = 1024: alpha has the shift structure (coupling_gemm_bf16x3_shift)
     const float* omega;     // [B][N]
     const float* kn_env;    // [B] float32(K_b / N), per-env coupling gain
     const double* g_stim;   // [B][n_elec][N]
@@ -459,6 +460,103 @@ __device__ __forceinline__ void coupling_gemm_bf16x3(const float* __restrict__ X
     }
 }
 
+// The same GEMM at TPW = 4 (N = 1024) for an alpha with the grid's shift
+// structure (alpha_shift_reuse, kura_capi.inc; DevParams.alpha_reuse):
+//   fragment(jt, b) == fragment(jt - 1, b - 2)   for jt % 4 != 0 and b % 8 >= 2,
+// which every alpha = f(grid distance) on the 16 x 8 x 8 grid has -- a wave's
+// four tiles are four x-lines each of one z-plane, a k-block b = 8 zk + xb is
+// x-lines 2xb, 2xb+1 of plane zk, so a fragment depends on |z_wave - zk| and
+// on the displacement d = xb - 2t alone.  Within a group of 8 k-blocks (one
+// zk) d takes 14 values, and at any block the live ones are 8 consecutive:
+// the fragment of displacement d lives in physical set (d + 6) mod 8, named
+// statically (the 8 blocks fully unrolled), and tile t at block xb reads set
+// (xb - 2t + 6) mod 8 -- what tile t-1 read two blocks earlier.  Loaded are
+// only tile 0's fragments and blocks 0, 1 of a group: 14 sets per group
+// instead of 32 (360 loads per sweep instead of the two-block ring's 792,
+// both counting their clamped, unused tail prefetch), no moves, no LDS, no
+// scalar loads, the same 96 VGPRs as the two-block ring.
+//   after block xb < 6: tile 3's set (xb) has died, it takes tile 0's
+//     fragment of block xb + 2 (d = xb + 2, the same set);
+//   after blocks 6, 7: all four sets have died; tile t's takes tile t+1's
+//     (mod 4) fragment of the next group's block xb - 6.
+// The tiles of a block run 3, 2, 1, 0: the mid-group refill issues first and
+// is read last, two blocks later.  Per tile the k-blocks ascend and each is
+// the six products in the oracle's order, so every acc[t] sees the sequence
+// of coupling_gemm_bf16x3 and the sums are bit-identical.
+__device__ __forceinline__ void coupling_gemm_bf16x3_shift(const float* __restrict__ Xs,
+                                                           const float* __restrict__ alpha_sw, floatx16 (&acc)[4],
+                                                           unsigned long long* dbg = nullptr) {
+    (void)dbg;
+    constexpr int TPW = 4;
+    constexpr int N = TPW * 32 * NWAVES;
+    constexpr int NB = N / 16;
+    constexpr int GB = 8;                       // k-blocks per group (one z-plane of the operand)
+    constexpr int TSTRIDE = NB * 3 * 64 * 16;   // bytes per column tile
+    static_assert(NB % GB == 0, "whole groups");
+    int lane;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+#pragma unroll
+    for (int t = 0; t < TPW; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+    const floatx4* xs4 = reinterpret_cast<const floatx4*>(Xs + (lane >> 5) * XS_HALF + (lane & 31) * 4);
+    const float* au = uniform_ptr(alpha_sw);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)((const char*)au + (size_t)wave * TPW * TSTRIDE), 0, TPW * TSTRIDE, 0x00020000);
+    auto ld = [&](int t, int b, int p) -> bf16x8 {
+        KDBG_CHECK(dbg, t >= 0 && t < TPW && b >= 0 && b < NB &&
+                            ((b * 3 + p) * 64 + lane) * 16 + t * TSTRIDE + 16 <= TPW * TSTRIDE);
+        return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, ((b * 3 + p) * 64 + lane) * 16,
+                                                                                 t * TSTRIDE, 0));
+    };
+    bf16x8 a1[GB], a2[GB], a3[GB];
+#pragma unroll
+    for (int d = 0; d < 2; ++d)
+#pragma unroll
+        for (int t = 0; t < TPW; ++t) {
+            const int s = (d - 2 * t + 6) & 7;
+            a1[s] = ld(t, d, 0);
+            a2[s] = ld(t, d, 1);
+            a3[s] = ld(t, d, 2);
+        }
+#pragma unroll 1
+    for (int b0 = 0; b0 < NB; b0 += GB) {
+#pragma unroll
+        for (int xb = 0; xb < GB; ++xb) {
+            bf16x8 x1, x2, x3;
+            split_bf16x3(xs4[(2 * (b0 + xb)) * (XS_BLOCK / 4)], xs4[(2 * (b0 + xb) + 1) * (XS_BLOCK / 4)], x1, x2, x3);
+#pragma unroll
+            for (int t = TPW - 1; t >= 0; --t) {
+                const int s = (xb - 2 * t + 6) & 7;
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a1[s], acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a2[s], acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a1[s], acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a3[s], acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a2[s], acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, a1[s], acc[t], 0, 0, 0);
+                if (xb < GB - 2) {
+                    if (t == TPW - 1) {   // the one set that died: tile 0's fragment of block xb + 2
+                        a1[s] = ld(0, b0 + xb + 2, 0);
+                        a2[s] = ld(0, b0 + xb + 2, 1);
+                        a3[s] = ld(0, b0 + xb + 2, 2);
+                    }
+                } else {   // the next group's blocks 0, 1
+                    // (the last group loads its own again, unused: a branch
+                    // around these loads makes the waits of blocks 6, 7 cover
+                    // the path without them -- vmcnt(0..2), which drains the
+                    // prefetch on every other group)
+                    const int tn = (t + 1) & 3, bn = (b0 + GB < NB ? b0 + GB : b0) + xb - (GB - 2);
+                    a1[s] = ld(tn, bn, 0);
+                    a2[s] = ld(tn, bn, 1);
+                    a3[s] = ld(tn, bn, 2);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
 // KURA_COUPLING_F32: exact fp32, the k-ordered fmaf chain of
 // v_mfma_f32_32x32x2_f32.  Wave w owns column tiles w*TPW .. w*TPW+TPW-1.
 template <int TPW>
@@ -605,12 +703,20 @@ __device__ __forceinline__ void coupling_gemm_bf16x3_dd(const float* __restrict_
 }
 
 // The coupling GEMM of a handle's arithmetic (SP: KURA_COUPLING_BF16X3).
+// reuse (DevParams.alpha_reuse, decided by the host from the data): alpha has
+// the shift structure, BF16X3 at TPW = 4 takes coupling_gemm_bf16x3_shift.
 template <int TPW, bool SP>
 __device__ __forceinline__ void coupling_gemm(const float* __restrict__ Xs, const float* __restrict__ alpha_sw,
-                                              floatx16 (&acc)[TPW], unsigned long long* dbg = nullptr) {
-    if constexpr (SP)
+                                              int reuse, floatx16 (&acc)[TPW], unsigned long long* dbg = nullptr) {
+    if constexpr (SP) {
+        if constexpr (TPW == 4) {
+            if (__builtin_amdgcn_readfirstlane(reuse)) {   // wave-uniform: a scalar branch
+                coupling_gemm_bf16x3_shift(Xs, alpha_sw, acc, dbg);
+                return;
+            }
+        }
         coupling_gemm_bf16x3<TPW>(Xs, alpha_sw, acc, dbg);
-    else
+    } else
         coupling_gemm_f32<TPW>(Xs, alpha_sw, acc, dbg);
 }
 
@@ -2447,7 +2553,7 @@ __device__ KURA_SOLVE_ATTR void solve_wg(DevParamsK& __restrict__ pin, float* Xs
                 coupling_gemm_xl<TPW>(xgrp, p.alpha_sw, Xs, NG, col0, acc STAMP_ARGS);
         } else {
 #ifdef KURA_DEBUG
-            coupling_gemm<TPW, SP>(Xs, p.alpha_sw, acc, uniform_ptr(p.stats));
+            coupling_gemm<TPW, SP>(Xs, p.alpha_sw, p.alpha_reuse, acc, uniform_ptr(p.stats));
             if (p.gemm_dump && blockIdx.x == 0 && nrhs < p.gemm_dump_n) {   // the sweep's operand and sums
                 float* d = p.gemm_dump + (size_t)nrhs * 2 * 32 * N;
                 for (int idx = tid; idx < 32 * N; idx += NTHREADS) d[idx] = Xs[xs_idx(idx / N, idx % N)];
@@ -2464,7 +2570,7 @@ __device__ KURA_SOLVE_ATTR void solve_wg(DevParamsK& __restrict__ pin, float* Xs
                 coupling_gemm_bf16x3_dd<TPW>(Xs, p.alpha_dd, p.alpha_dd_bytes, acc);
             else
 #endif
-                coupling_gemm<TPW, SP>(Xs, p.alpha_sw, acc);
+                coupling_gemm<TPW, SP>(Xs, p.alpha_sw, p.alpha_reuse, acc);
 #endif
         }
         STAMP(2);
@@ -3157,7 +3263,7 @@ __global__ void kura_selftest_math_kernel(const float* x, const float* y, float*
 // One 32-row coupling GEMM through the production GEMM path.
 template <int TPW, bool SP>
 __global__ __launch_bounds__(NTHREADS) void kura_selftest_gemm_kernel(const float* X, const float* alpha_sw,
-                                                                       float* Y, int N) {
+                                                                       float* Y, int N, int reuse) {
     extern __shared__ float Xs[];
     for (int idx = threadIdx.x; idx < 32 * N; idx += blockDim.x) {
         const int r = idx / N, k = idx % N;
@@ -3165,7 +3271,7 @@ __global__ __launch_bounds__(NTHREADS) void kura_selftest_gemm_kernel(const floa
     }
     __syncthreads();
     floatx16 acc[TPW];
-    coupling_gemm<TPW, SP>(Xs, alpha_sw, acc);
+    coupling_gemm<TPW, SP>(Xs, alpha_sw, reuse, acc);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int t = 0; t < TPW; ++t)

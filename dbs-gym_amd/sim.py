@@ -133,6 +133,13 @@ class KuraSim:
             raise ValueError(f"alpha shape {a.shape} != ({self.N}, {self.N})")
         check(self.lib, self.lib.kura_set_coupling(self._h, a.ctypes.data), "kura_set_coupling")
 
+    def alpha_reuse(self) -> bool:
+        """Whether the step's GEMM reuses alpha fragments across a wave's tiles
+        (kura.h kura_alpha_reuse: BF16X3 at N = 1024 on a grid-structured alpha)."""
+        rc = self.lib.kura_alpha_reuse(self._h)
+        check(self.lib, min(rc, 0), "kura_alpha_reuse")
+        return rc == 1
+
     def set_env_params(self, omega, g_stim, g_rec=None, env0: int = 0) -> None:
         w = np.ascontiguousarray(omega, dtype=np.float32)
         n = w.shape[0]

@@ -165,6 +165,18 @@ int kura_abi_version(void);
 
 /* setup (host pointers, synchronous) */
 int kura_set_coupling(KuraHandle* h, const float* alpha /* N*N row-major, alpha[i][j] */);
+/* BF16X3 at N = 1024: kura_set_coupling looks at the data on every call.  An
+ * alpha whose B fragments repeat along the grid (fragment(jt, b) ==
+ * fragment(jt-1, b-2) for jt%4 != 0, b%8 >= 2 -- every alpha = f(distance) on
+ * the reference's 16x8x8 grid) lets the step's GEMM reuse a wave's fragments
+ * across its four tiles instead of loading each; the sums are bit-identical.
+ * Any other alpha takes the general GEMM, as does every alpha with
+ * KURA_ALPHA_REUSE=0 in the environment.
+ * kura_alpha_reuse: 1 / 0, the form the handle's step takes (a negative
+ * KURA_E_* on a null handle).  kura_alpha_reuse_detect: the same decision from
+ * the data alone (pure host code, no device call; 0 for n_osc != 1024). */
+int kura_alpha_reuse(KuraHandle* h);
+int kura_alpha_reuse_detect(const float* alpha, int n_osc);
 int kura_set_env_params(KuraHandle* h, int env0, int n,
                         const float* omega,   /* n*N  (float32 cast of w0, env.py:264) */
                         const double* g_stim, /* n*n_elec*N conductances, env.py:106-120 */
@@ -316,6 +328,8 @@ int kura_selftest_math(const float* x, const float* y, float* out, int n);
 int kura_selftest_gemm(const float* X, const float* alpha, float* Y, int N);   /* KURA_COUPLING_F32 */
 /* the same through the GEMM of a coupling arithmetic (KURA_COUPLING_*; AUTO = BF16X3 at these N) */
 int kura_selftest_coupling(const float* X, const float* alpha, float* Y, int N, int coupling);
+/* 1 / 0: whether the last kura_selftest_coupling took the fragment-reuse GEMM (kura_alpha_reuse) */
+int kura_selftest_alpha_reuse(void);
 /* per-wave phase cycle counters of a -DKURA_STAMPS build ([8 waves][16]:
  * stage-input, barrier, GEMM, epilogue, barrier, post-step error pass, flag,
  * post-step decision, saves, FSAL, time advance, 5 spare; tools/phase_stamps.py);
