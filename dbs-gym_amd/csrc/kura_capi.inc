@@ -346,11 +346,7 @@ static size_t coupling_image_alloc(int N, bool sp, int tpw) {
 // dynamic LDS of a launch: the 32 x N operand, or (split groups) the two
 // streamed chunk images of the XL GEMM, which also hold the part's own image
 static size_t launch_lds(const KuraHandle* h) {
-    return (size_t)(h->xl ? 2 * XL_CIMG : xs_floats(h->tpw * 256)) * sizeof(float)
-#if KURA_EXP_ALPHA == 3
-           + (h->xl ? 0 : 8192)   // measurement build: the LDS gather table after the operand
-#endif
-        ;
+    return (size_t)(h->xl ? 2 * XL_CIMG : xs_floats(h->tpw * 256)) * sizeof(float);
 }
 
 // The step / reset kernels of a handle: (TPW, split groups, coupling).

@@ -18,6 +18,18 @@
 //     over the window the R64 order (kura_detmath.h).
 // The arithmetic is a bit-exact twin of oracle/kura_oracle.c; this file must
 // be compiled with -ffp-contract=off (see __graft_entry__.build).
+
+// Build switches of settled experiments: their code is gone (DESIGN.md section
+// 5, "Retired build switches": what each did, its result, where the A/B is
+// kept).  A command line that still passes one must not build the product and
+// label it a variant.
+#if defined(KURA_EXP_ALPHA) || defined(KURA_EXP_ORDER) || defined(KURA_EXP_NO_B1) || defined(KURA_EXP_NO_B2) || \
+    defined(KURA_SPLIT_SCALAR) || defined(KURA_SI_PACKED) || defined(KURA_GROUPSUM_ATOMIC) ||                   \
+    defined(KURA_FUSED_ERR) || defined(KURA_SAVE_PACKED) || defined(KURA_SOLVE_INLINE) ||                       \
+    defined(KURA_RESET_DEDUP) || defined(KURA_REC_LD_AUX) || defined(KURA_REC_ST_AUX) || defined(KURA_BITSEL)
+#error "retired build switch (KURA_EXP_ALPHA, KURA_EXP_ORDER, KURA_EXP_NO_B1, KURA_EXP_NO_B2, KURA_SPLIT_SCALAR, KURA_SI_PACKED, KURA_GROUPSUM_ATOMIC, KURA_FUSED_ERR, KURA_SAVE_PACKED, KURA_SOLVE_INLINE, KURA_RESET_DEDUP, KURA_REC_LD_AUX, KURA_REC_ST_AUX, KURA_BITSEL): see DESIGN.md, 'Retired build switches'"
+#endif
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -66,7 +78,7 @@ struct DevParams {
     double bw_b[5], bw_a[5], bw_zi[4];
     float rtol, atol, kn, dt0;
     const float* alpha_sw;  // B-fragment swizzled coupling
-    const float* alpha_dd;  // BF16X3, N <= 1024: the deduplicated image too (the reset's GEMM, -DKURA_RESET_DEDUP)
+    const float* alpha_dd;  // BF16X3, N <= 1024: the deduplicated image too (the reset's GEMM, coupling_gemm_bf16x3_dd)
     unsigned alpha_dd_bytes;  // its size (the GEMM's descriptor range)
     int alpha_reuse;        // BF16X3, N = 1024: alpha has the shift structure (coupling_gemm_bf16x3_shift)
     const float* omega;     // [B][N]
@@ -172,34 +184,16 @@ __shared__ double s_smp_r[E_WG][KURA_S_MAX + 2];
 #define XL_KC 512                        // oscillators per streamed GEMM chunk
 #define XL_CIMG (XL_KC / 8 * XS_BLOCK)   // floats of one chunk image
 #define XL_SPIN_MAX (1u << 25)
-// alpha ring depth (k-blocks) of the split-group GEMM at TPW = 1 / 2
-#ifndef KURA_XL_DEPTH1
-#define KURA_XL_DEPTH1 8
-#endif
-#ifndef KURA_XL_DEPTH2
-#define KURA_XL_DEPTH2 8
-#endif
-#ifndef KURA_XL_DEPTH4
-#define KURA_XL_DEPTH4 4
-#endif
+// alpha ring depth (k-blocks) of the split-group GEMM at TPW = 1 / 2 / 4
+constexpr int KURA_XL_DEPTH1 = 8, KURA_XL_DEPTH2 = 8, KURA_XL_DEPTH4 = 4;
 // split groups in BF16X3: parts of up to KURA_XL_SP_STAGED_MAXTPW * 256
 // oscillators stage the split operand and split alpha in registers
 // (coupling_gemm_xl_bf16x3); larger parts split per k-block with pre-split,
 // deduplicated alpha (coupling_gemm_xl_bf16x3_kb); same-box A/B,
 // profiles/r05_dedup_and_xl_forms_ab.txt
-#ifndef KURA_XL_SP_STAGED_MAXTPW
-#define KURA_XL_SP_STAGED_MAXTPW 1
-#endif
+constexpr int KURA_XL_SP_STAGED_MAXTPW = 1;
 // ... and the alpha ring of the bf16x3 forms, in 16-deep k-blocks (12 VGPRs per tile each)
-#ifndef KURA_XL_SP_DEPTH1
-#define KURA_XL_SP_DEPTH1 8
-#endif
-#ifndef KURA_XL_SP_DEPTH2
-#define KURA_XL_SP_DEPTH2 4
-#endif
-#ifndef KURA_XL_SP_DEPTH4
-#define KURA_XL_SP_DEPTH4 2
-#endif
+constexpr int KURA_XL_SP_DEPTH1 = 8, KURA_XL_SP_DEPTH2 = 4, KURA_XL_SP_DEPTH4 = 2;
 __host__ __device__ constexpr int xs_floats(int N) { return (N / 8) * XS_BLOCK; }
 // floats of one part's LDS / global sin/cos image (TPW column tiles per wave)
 __host__ __device__ constexpr int xl_img(int tpw) { return xs_floats(tpw * 256); }
@@ -267,11 +261,10 @@ __device__ __forceinline__ T* uniform_ptr(T* ptr) {
 // k order of the fp32 operand image, so the sin/cos rows are split from the
 // same two float4 reads of the LDS operand.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#ifndef KURA_SPLIT_SCALAR
 // Pairwise: one v_cvt_pk_bf16_f32 (round to nearest even) per two values and
 // part, the bf16 pair widened back by a shift and a mask, the residual by one
-// v_pk_add_f32 -- 9 VALU per pair.  The same values as the scalar form (each
-// residual x - bf16(x) is exact in fp32).
+// v_pk_add_f32 -- 9 VALU per pair.  The same values as converting element by
+// element (each residual x - bf16(x) is exact in fp32).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -296,33 +289,21 @@ __device__ __forceinline__ void split_bf16x3(floatx4 lo, floatx4 hi, bf16x8& h1,
     h2 = __builtin_bit_cast(bf16x8, b);
     h3 = __builtin_bit_cast(bf16x8, c);
 }
-#else
-__device__ __forceinline__ void split_bf16x3(floatx4 lo, floatx4 hi, bf16x8& h1, bf16x8& h2, bf16x8& h3) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float x = i < 4 ? lo[i] : hi[i - 4];
-        const __bf16 a = (__bf16)x;
-        const float r1 = x - (float)a;
-        const __bf16 b = (__bf16)r1;
-        h1[i] = a;
-        h2[i] = b;
-        h3[i] = (__bf16)(r1 - (float)b);
-    }
-}
-#endif
 
-// KURA_EXP_ALPHA (measurement builds only, wrong sums): 1 = every k-block
-// reads block 0's fragments (alpha L1-resident, same instructions), 2 = no
-// refill loads at all -- upper bounds of what alpha locality could gain;
-// 3 = the fragments gathered from a grid-displacement table in LDS (8 KB
-// after the operand, filled with split hashed values: the access pattern,
-// instruction mix and operand bit density of an exact table gather with 64
-// of its 128 classes).  KURA_EXP_ORDER (measurement builds only, a different
-// accumulation order than the oracle's): 1 / 2 group the six products by
-// their A / B operand -- does MFMA operand switching cost power here?
-#ifndef KURA_EXP_ALPHA
-#define KURA_EXP_ALPHA 0
-#endif
+// One 16-deep k-block of a BF16X3 tile: the six part products in the order of
+// the oracle's oracle_split_gemm_rows (x1a1, x1a2, x2a1, x1a3, x2a2, x3a1).
+// The order is the numerics contract (the MFMA's accumulation is not
+// associative); every BF16X3 GEMM body below states it through this helper.
+__device__ __forceinline__ void mfma6_bf16x3(bf16x8 x1, bf16x8 x2, bf16x8 x3, bf16x8 a1, bf16x8 a2, bf16x8 a3,
+                                             floatx16& acc) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a1, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a2, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a1, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a3, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a2, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, a1, acc, 0, 0, 0);
+}
+
 template <int TPW>
 __device__ __forceinline__ void coupling_gemm_bf16x3(const float* __restrict__ Xs, const float* __restrict__ alpha_sw,
                                                      floatx16 (&acc)[TPW], unsigned long long* dbg = nullptr) {
@@ -343,58 +324,9 @@ __device__ __forceinline__ void coupling_gemm_bf16x3(const float* __restrict__ X
         (void*)((const char*)au + (size_t)wave * TPW * TSTRIDE), 0, TPW * TSTRIDE, 0x00020000);
     auto ld = [&](int t, int b, int p) -> bf16x8 {
         KDBG_CHECK(dbg, b >= 0 && b < NB && ((b * 3 + p) * 64 + lane) * 16 + t * TSTRIDE + 16 <= TPW * TSTRIDE);
-#if KURA_EXP_ALPHA == 1   // measurement only (wrong sums): every k-block reads block 0 -- alpha L1-resident
-        b = 0;
-#endif
         return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, ((b * 3 + p) * 64 + lane) * 16,
                                                                                  t * TSTRIDE, 0));
     };
-#if KURA_EXP_ALPHA == 3
-    typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-    u32x2_t* tab = reinterpret_cast<u32x2_t*>(const_cast<float*>(Xs) + xs_floats(N));
-    // each wave writes the whole table: three-way bf16 splits of hashed values
-    // in (-0.9, 0.9), so the MFMA operands carry as many set bits as real alpha
-    for (int i = lane; i < 1024; i += 64) {
-        unsigned hs = (unsigned)(i + 1) * 2654435761u;
-        hs ^= hs >> 15;
-        hs *= 2246822519u;
-        hs ^= hs >> 13;
-        const float v = ((float)(hs & 0xffffffu) / 8388608.0f - 1.0f) * 0.9f;
-        const __bf16 a = (__bf16)v;
-        const float r1 = v - (float)a;
-        const __bf16 b = (__bf16)r1;
-        const __bf16 c = (__bf16)(r1 - (float)b);
-        tab[i] = u32x2_t{(unsigned)__builtin_bit_cast(unsigned short, a) |
-                             ((unsigned)__builtin_bit_cast(unsigned short, b) << 16),
-                         (unsigned)__builtin_bit_cast(unsigned short, c)};
-    }
-    const int j0 = 7 - (lane & 7) + (lane >> 5);
-    int xc[TPW], zc[TPW];
-#pragma unroll
-    for (int t = 0; t < TPW; ++t) {
-        const int line = 4 * (wave * TPW + t) + ((lane & 31) >> 3);
-        xc[t] = line & 15;
-        zc[t] = line >> 4;
-    }
-    auto gth = [&](int t, int b, bf16x8& q1, bf16x8& q2, bf16x8& q3) __attribute__((always_inline)) {
-        const int xk = (2 * b) & 15, zk = (2 * b) >> 4;
-        const int dz = __builtin_abs(zc[t] - zk) * 16;
-        const int c0 = (dz + __builtin_abs(xc[t] - xk)) & 63, c1 = (dz + __builtin_abs(xc[t] - xk - 1)) & 63;
-        const u32x2_t* r0 = tab + c0 * 16 + j0;
-        const u32x2_t* r1 = tab + c1 * 16 + j0;
-        const u32x2_t e[8] = {r0[0], r0[2], r0[4], r0[6], r1[0], r1[2], r1[4], r1[6]};
-        u32x4 w1, w2, w3;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            w1[q] = __builtin_amdgcn_perm(e[2 * q + 1].x, e[2 * q].x, 0x05040100u);
-            w2[q] = __builtin_amdgcn_perm(e[2 * q + 1].x, e[2 * q].x, 0x07060302u);
-            w3[q] = __builtin_amdgcn_perm(e[2 * q + 1].y, e[2 * q].y, 0x05040100u);
-        }
-        q1 = __builtin_bit_cast(bf16x8, w1);
-        q2 = __builtin_bit_cast(bf16x8, w2);
-        q3 = __builtin_bit_cast(bf16x8, w3);
-    };
-#endif
     // two register sets per tile: block b+2's parts load right after block
     // b's MFMAs, a whole block of cover (one set: the loads issue after the
     // block's last x3*a1 and the next block's first MFMA waits on them;
@@ -404,13 +336,9 @@ __device__ __forceinline__ void coupling_gemm_bf16x3(const float* __restrict__ X
     for (int d = 0; d < 2; ++d)
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
-#if KURA_EXP_ALPHA == 3
-            gth(t, d, a1[d][t], a2[d][t], a3[d][t]);
-#else
             a1[d][t] = ld(t, d < NB ? d : NB - 1, 0);
             a2[d][t] = ld(t, d < NB ? d : NB - 1, 1);
             a3[d][t] = ld(t, d < NB ? d : NB - 1, 2);
-#endif
         }
     auto blk = [&](int b, int d) __attribute__((always_inline)) {
         bf16x8 x1, x2, x3;
@@ -418,37 +346,10 @@ __device__ __forceinline__ void coupling_gemm_bf16x3(const float* __restrict__ X
         const int bn = b + 2 < NB ? b + 2 : NB - 1;
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
-#if KURA_EXP_ORDER == 1   // measurement only (a different accumulation order): A operand held for 3, 2, 1 MFMAs
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a1[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a2[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a3[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a1[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a2[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, a1[d][t], acc[t], 0, 0, 0);
-#elif KURA_EXP_ORDER == 2   // measurement only: B operand held for 3, 2, 1 MFMAs
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a1[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a1[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, a1[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a2[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a2[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a3[d][t], acc[t], 0, 0, 0);
-#else
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a1[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a2[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a1[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a3[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a2[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, a1[d][t], acc[t], 0, 0, 0);
-#endif
-#if KURA_EXP_ALPHA == 3
-            gth(t, bn, a1[d][t], a2[d][t], a3[d][t]);
-#elif KURA_EXP_ALPHA != 2   // (measurement only, wrong sums: =2 keeps the first two blocks' fragments, no alpha traffic)
+            mfma6_bf16x3(x1, x2, x3, a1[d][t], a2[d][t], a3[d][t], acc[t]);
             a1[d][t] = ld(t, bn, 0);
             a2[d][t] = ld(t, bn, 1);
             a3[d][t] = ld(t, bn, 2);
-#else
-            (void)bn;
-#endif
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -529,12 +430,7 @@ __device__ __forceinline__ void coupling_gemm_bf16x3_shift(const float* __restri
 #pragma unroll
             for (int t = TPW - 1; t >= 0; --t) {
                 const int s = (xb - 2 * t + 6) & 7;
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a1[s], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a2[s], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a1[s], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a3[s], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a2[s], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, a1[s], acc[t], 0, 0, 0);
+                mfma6_bf16x3(x1, x2, x3, a1[s], a2[s], a3[s], acc[t]);
                 if (xb < GB - 2) {
                     if (t == TPW - 1) {   // the one set that died: tile 0's fragment of block xb + 2
                         a1[s] = ld(0, b0 + xb + 2, 0);
@@ -634,14 +530,15 @@ __device__ __forceinline__ void coupling_gemm_f32(const float* __restrict__ Xs, 
 // resident).  Same fragments, same MFMAs in the same order as
 // coupling_gemm_bf16x3, so the sums are identical; the fragment offsets are
 // scalar loads one k-block ahead of the refill they serve.  Used by the
-// reset (KURA_RESET_DEDUP): over its ~457 sweeps the workgroups of an XCD
-// drift apart and the 6 MiB streamed image misses L2.
+// reset (solve_wg): over its ~457 sweeps the workgroups of an XCD drift apart
+// and the 6 MiB streamed image misses L2; warm B=4096 env0
+// reset 56.3 -> 53.3 ms, same box (profiles/r06_reset_dedup_ab.txt).  The
+// step keeps the streamed image: the scalar-loaded map cost it 7 %.
 template <int TPW>
 __device__ __forceinline__ void coupling_gemm_bf16x3_dd(const float* __restrict__ Xs, const float* __restrict__ alpha_dd,
                                                         unsigned img_bytes, floatx16 (&acc)[TPW]) {
     constexpr int N = TPW * 32 * NWAVES;
     constexpr int NB = N / 16, NT = N / 32;
-    constexpr unsigned FRAG = 3 * 64 * 16;
     int lane;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -651,7 +548,6 @@ __device__ __forceinline__ void coupling_gemm_bf16x3_dd(const float* __restrict_
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
     const floatx4* xs4 = reinterpret_cast<const floatx4*>(Xs + (lane >> 5) * XS_HALF + (lane & 31) * 4);
     const float* au = uniform_ptr(alpha_dd);
-    (void)FRAG;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)au, 0, __builtin_amdgcn_readfirstlane(img_bytes), 0x00020000);   // map + distinct fragments
     // the map through the constant address space: scalar loads (s_load_dword)
@@ -680,12 +576,7 @@ __device__ __forceinline__ void coupling_gemm_bf16x3_dd(const float* __restrict_
         const int bn3 = b + 3 < NB ? b + 3 : NB - 1;
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a1[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a2[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a1[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a3[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a2[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, a1[d][t], acc[t], 0, 0, 0);
+            mfma6_bf16x3(x1, x2, x3, a1[d][t], a2[d][t], a3[d][t], acc[t]);
             const int o = om[t];
             a1[d][t] = ld(o, 0);
             a2[d][t] = ld(o, 1);
@@ -719,14 +610,6 @@ __device__ __forceinline__ void coupling_gemm(const float* __restrict__ Xs, cons
     } else
         coupling_gemm_f32<TPW>(Xs, alpha_sw, acc, dbg);
 }
-
-// the reset's GEMM reads the deduplicated alpha image (coupling_gemm_bf16x3_dd):
-// same box, warm B=4096 env0 reset 56.3 -> 53.3 ms, step unchanged
-// (profiles/r06_reset_dedup_ab.txt); -DKURA_RESET_DEDUP=0 streams the plain image
-#ifndef KURA_RESET_DEDUP
-#define KURA_RESET_DEDUP 1
-#endif
-
 
 // Workgroup barrier that orders LDS only.  Inside a solve every workspace
 // record (R) is written and read back by the same lane (MFMA-layout
@@ -924,14 +807,7 @@ __device__ __forceinline__ void coupling_gemm_xl_bf16x3_kb(const float* __restri
         bf16x8 x1, x2, x3;
         split_bf16x3(lo, hi, x1, x2, x3);
 #pragma unroll
-        for (int t = 0; t < TPW; ++t) {
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, q1[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, q2[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, q1[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, q3[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, q2[d][t], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, q1[d][t], acc[t], 0, 0, 0);
-        }
+        for (int t = 0; t < TPW; ++t) mfma6_bf16x3(x1, x2, x3, q1[d][t], q2[d][t], q3[d][t], acc[t]);
         const int kn1 = kg0 + kb + XD + 1 < NB ? kg0 + kb + XD + 1 : NB - 1;
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
@@ -1076,12 +952,7 @@ __device__ __forceinline__ void coupling_gemm_xl_bf16x3(const float* __restrict_
             split_bf16x3(qlo[d][t], qhi[d][t], a1, a2, a3);
             qlo[d][t] = ldf(t, 2 * kn);
             qhi[d][t] = ldf(t, 2 * kn + 1);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a1, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a2, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a1, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, a3, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, a2, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x3, a1, acc[t], 0, 0, 0);
+            mfma6_bf16x3(x1, x2, x3, a1, a2, a3, acc[t]);
         }
     };
 #pragma unroll 1
@@ -1230,21 +1101,17 @@ __device__ __forceinline__ void split8(const floatx4& a, const floatx4& b, float
     v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
     v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
 }
-// cache policy (aux) of the record loads / stores: 0 = default; measurement
-// builds set 2 (nt) to keep the record stream from evicting alpha in L2
-#ifndef KURA_REC_LD_AUX
-#define KURA_REC_LD_AUX 0
-#endif
-#ifndef KURA_REC_ST_AUX
-#define KURA_REC_ST_AUX 0
-#endif
+// (record loads / stores keep the default cache policy, aux 0: nt, meant to
+// keep the record stream from evicting alpha in L2, cost 3.6 % on the loads
+// -- a lane's re-reads of its records hit L2 -- and 0.7 % on the stores,
+// profiles/r06_record_nt_ab.txt)
 // lane's two env groups: half 0 -> envs 4h..4h+3, half 1 -> envs 8+4h..8+4h+3
 __device__ __forceinline__ void load8(const Slot& w, int slot, int t, float (&v)[8]) {
     w.check(slot, t);
     const floatx4 a = __builtin_bit_cast(
-        floatx4, __builtin_amdgcn_raw_buffer_load_b128(w.rs, w.voff, w.soff(slot, t), KURA_REC_LD_AUX));
+        floatx4, __builtin_amdgcn_raw_buffer_load_b128(w.rs, w.voff, w.soff(slot, t), 0));
     const floatx4 b = __builtin_bit_cast(
-        floatx4, __builtin_amdgcn_raw_buffer_load_b128(w.rs, w.voff + 1024, w.soff(slot, t), KURA_REC_LD_AUX));
+        floatx4, __builtin_amdgcn_raw_buffer_load_b128(w.rs, w.voff + 1024, w.soff(slot, t), 0));
     split8(a, b, v);
 }
 // Store-data hazard ("The round-2 miscompiles,
@@ -1267,8 +1134,7 @@ __device__ __forceinline__ int opaque_vgpr(int v) {
     return v;
 }
 __device__ __forceinline__ void store_rec_b128(const floatx4& v, __amdgpu_buffer_rsrc_t rs, int voff, int soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, v), rs, opaque_vgpr(voff) + soff, 0,
-                                           KURA_REC_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, v), rs, opaque_vgpr(voff) + soff, 0, 0);
 }
 __device__ __forceinline__ void store8(const Slot& w, int slot, int t, const float (&v)[8]) {
     // raw buffer stores through the same wave-uniform descriptor as the
@@ -1331,68 +1197,9 @@ __device__ __forceinline__ void coupling_epilogue(DevParamsK& __restrict__ p, co
     }
 }
 
-// Stage input ys = y0 + chain_j(A[s][j] * h*f_j) (zero coefficients skipped,
-// as in the oracle), theta = fmod(ys, 2pi), sin/cos into the LDS operand.
-// Stage 0 is the solve's initial RHS at y0.  Tiles are software-pipelined:
-// the records of tile t+1 are requested before tile t is computed.  Every
-// f_j comes from its record, the newest (f_{s-1}) included: handing it over
-// in registers from the epilogue (round 1) only made the compiler spill it
-// across the stage barrier -- 32 dwords per lane per sweep to scratch and
-// back -- and cost 4 % of the step (DESIGN.md section 5, K1).
 // ys = y0 + chain_j(kA[S][j] * (h f_j)), j < S, zero coefficients skipped
 // (the oracle's order: fp32 products h*f_j, the first term a product, the
 // rest fmas, then y0 + the chain)
-// Packed FP32 pairs (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32: two IEEE
-// operations per instruction): the same operations in the same order as the
-// scalar forms they pair (kura_detmath.h), so the results are identical.
-typedef float kf2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ kf2 kf2_fma(kf2 a, kf2 b, kf2 c) { return __builtin_elementwise_fma(a, b, c); }
-// kdm_fold_reduce + kdm_sincos_red of two elements
-__device__ __forceinline__ void sincos_fold2(kf2 y, kf2& sn, kf2& cs, int& slow) {
-    const kf2 k = __builtin_elementwise_trunc(y * KDM_INV_TWO_PI_F);
-    const kf2 n = __builtin_elementwise_rint(y * KDM_TWO_OVER_PI_F);
-    const int j0 = (int)n.x - 4 * (int)k.x, j1 = (int)n.y - 4 * (int)k.y;
-    const kf2 jf = {(float)j0, (float)j1};
-    kf2 r = kf2_fma(-n, kf2(KDM_PIO2_C1), y);
-    r = kf2_fma(-jf, kf2(KDM_PIO2_C2), r);
-    r = kf2_fma(-jf, kf2(KDM_PIO2_C3), r);
-    slow |= (int)!(fabsf(y.x) < 4194304.0f) | (int)!(fabsf(y.y) < 4194304.0f);
-    const kf2 z = r * r;
-    kf2 ps = kf2_fma(z, kf2(-1.9515295891e-4f), kf2(8.3321608736e-3f));
-    ps = kf2_fma(z, ps, kf2(-1.6666654611e-1f));
-    const kf2 sr = kf2_fma(r * z, ps, r);
-    kf2 pc = kf2_fma(z, kf2(2.443315711809948e-5f), kf2(-1.388731625493765e-3f));
-    pc = kf2_fma(z, pc, kf2(4.166664568298827e-2f));
-    const kf2 cr = kf2_fma(z * z, pc, kf2_fma(kf2(-0.5f), z, kf2(1.0f)));
-    const int q0 = j0 & 3, q1 = j1 & 3;
-    float s0 = (q0 & 1) ? cr.x : sr.x, c0 = (q0 & 1) ? sr.x : cr.x;
-    float s1 = (q1 & 1) ? cr.y : sr.y, c1 = (q1 & 1) ? sr.y : cr.y;
-    s0 = (q0 & 2) ? -s0 : s0;
-    s1 = (q1 & 2) ? -s1 : s1;
-    c0 = ((q0 + 1) & 2) ? -c0 : c0;
-    c1 = ((q1 + 1) & 2) ? -c1 : c1;
-    sn = kf2{s0, s1};
-    cs = kf2{c0, c1};
-}
-// stage_ys of the element pair (q, q+1)
-template <int S>
-__device__ __forceinline__ kf2 stage_ys2(const float (&y0)[8], const float (&h)[8], const float (&f)[6][8], int q) {
-    const kf2 yy = {y0[q], y0[q + 1]};
-    if constexpr (S == 0) {
-        return yy;
-    } else {
-        const kf2 hh = {h[q], h[q + 1]};
-        auto hf = [&](int j) __attribute__((always_inline)) { return hh * kf2{f[j][q], f[j][q + 1]}; };
-        kf2 acc = kf2(kA[S][0]) * hf(0);
-        if constexpr (S > 1 && kA[S][1] != 0.0f) acc = kf2_fma(kf2(kA[S][1]), hf(1), acc);
-        if constexpr (S > 2) acc = kf2_fma(kf2(kA[S][2]), hf(2), acc);
-        if constexpr (S > 3) acc = kf2_fma(kf2(kA[S][3]), hf(3), acc);
-        if constexpr (S > 4) acc = kf2_fma(kf2(kA[S][4]), hf(4), acc);
-        if constexpr (S > 5) acc = kf2_fma(kf2(kA[S][5]), hf(5), acc);
-        return yy + acc;
-    }
-}
-
 template <int S>
 __device__ __forceinline__ void stage_ys(const float (&y0)[8], const float (&h)[8], const float (&f)[6][8],
                                          float (&ys)[8]) {
@@ -1412,22 +1219,14 @@ __device__ __forceinline__ void stage_ys(const float (&y0)[8], const float (&h)[
     }
 }
 
-template <int S>
-__device__ __forceinline__ void stage_ys_pk(const float (&y0)[8], const float (&h)[8], const float (&f)[6][8],
-                                            float (&ys)[8]) {
-#pragma unroll
-    for (int q = 0; q < 8; q += 2) {
-        const kf2 v = stage_ys2<S>(y0, h, f, q);
-        ys[q] = v.x;
-        ys[q + 1] = v.y;
-    }
-}
-#ifdef KURA_SI_PACKED
-#define STAGE_YS stage_ys_pk
-#else
-#define STAGE_YS stage_ys
-#endif
-
+// Stage input ys = y0 + chain_j(A[s][j] * h*f_j) (zero coefficients skipped,
+// as in the oracle), theta = fmod(ys, 2pi), sin/cos into the LDS operand.
+// Stage 0 is the solve's initial RHS at y0.  Tiles are software-pipelined:
+// the records of tile t+1 are requested before tile t is computed.  Every
+// f_j comes from its record, the newest (f_{s-1}) included: handing it over
+// in registers from the epilogue (round 1) only made the compiler spill it
+// across the stage barrier -- 32 dwords per lane per sweep to scratch and
+// back -- and cost 4 % of the step (DESIGN.md section 5, K1).
 template <int TPW>
 __device__ __forceinline__ void stage_input(const Slot& ws, float* Xs, int s STAMP_PARAMS) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1468,13 +1267,13 @@ __device__ __forceinline__ void stage_input(const Slot& ws, float* Xs, int s STA
         // lgkmcnt(0) wait per term and element, which also drained the LDS
         // writes of the tile before)
         switch (s) {
-            case 0: STAGE_YS<0>(y0[b], h, f[b], ys); break;
-            case 1: STAGE_YS<1>(y0[b], h, f[b], ys); break;
-            case 2: STAGE_YS<2>(y0[b], h, f[b], ys); break;
-            case 3: STAGE_YS<3>(y0[b], h, f[b], ys); break;
-            case 4: STAGE_YS<4>(y0[b], h, f[b], ys); break;
-            case 5: STAGE_YS<5>(y0[b], h, f[b], ys); break;
-            default: STAGE_YS<6>(y0[b], h, f[b], ys); break;
+            case 0: stage_ys<0>(y0[b], h, f[b], ys); break;
+            case 1: stage_ys<1>(y0[b], h, f[b], ys); break;
+            case 2: stage_ys<2>(y0[b], h, f[b], ys); break;
+            case 3: stage_ys<3>(y0[b], h, f[b], ys); break;
+            case 4: stage_ys<4>(y0[b], h, f[b], ys); break;
+            case 5: stage_ys<5>(y0[b], h, f[b], ys); break;
+            default: stage_ys<6>(y0[b], h, f[b], ys); break;
         }
         // theta = fmod(ys, 2pi_f) folded into the sincos reduction
         // (kdm_sincos_fmod2pi, kura_detmath.h): branch-free for the tile
@@ -1496,17 +1295,6 @@ __device__ __forceinline__ void stage_input(const Slot& ws, float* Xs, int s STA
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         STAMP(18);
-#elif defined(KURA_SI_PACKED)
-#pragma unroll
-        for (int q = 0; q < 8; q += 2) {
-            kf2 sn, cs;
-            sincos_fold2(kf2{ys[q], ys[q + 1]}, sn, cs, slow);
-            const int e0 = mfma_env(q, lane), e1 = mfma_env(q + 1, lane);
-            Xs[xs_idx(e0, i)] = sn.x;
-            Xs[xs_idx(16 + e0, i)] = cs.x;
-            Xs[xs_idx(e1, i)] = sn.y;
-            Xs[xs_idx(16 + e1, i)] = cs.y;
-        }
 #else
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -1684,19 +1472,6 @@ __device__ __forceinline__ void group_sum(DevParamsK& p, Part& pt, float (&vf)[N
     // wave 0 (a scalar branch): lanes >= E_WG get an offset past the
     // descriptor's range, which the hardware drops -- no exec-masked store
     // (hazards)
-#ifdef KURA_GROUPSUM_ATOMIC
-    // A/B form (round 5): relaxed agent-scope atomic stores by threads 0..15
-    if (tid < E_WG)
-        for (int k = 0; k < nk; ++k) {
-            __hip_atomic_store((gu32*)(xr + (part * RC + k) * E_WG + tid), __float_as_uint(vf[k]),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (with_d)
-                __hip_atomic_store((__attribute__((address_space(1))) unsigned long long*)(xd + (part * RC + k) *
-                                                                                              E_WG + tid),
-                                   (unsigned long long)__double_as_longlong(vd[k]), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        }
-#else
     if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
         constexpr int kSc1 = 16;          // cache policy: sc1 (write-through to memory)
         constexpr int kDrop = 0x7ffffff0;
@@ -1716,7 +1491,6 @@ __device__ __forceinline__ void group_sum(DevParamsK& p, Part& pt, float (&vf)[N
             }
         }
     }
-#endif
     group_barrier(p, pt);
     if (tid < E_WG)
         for (int k = 0; k < nk; ++k) {
@@ -1788,67 +1562,6 @@ __device__ __forceinline__ void err_dense_tile(const DP& p, const Slot& ws, int 
     store8(ws, SL_CC, t, cc);
 }
 
-// A/B form (-DKURA_FUSED_ERR): stage 6's coupling epilogue fused with
-// post_step's error pass -- f6 goes from the accumulators into the error
-// estimate and dense-output coefficients of its tile without a round trip
-// through its record, and the partials are published before the epilogue's
-// own barrier, which then also orders them (one pass and one barrier less
-// per Dopri step).  Same operations, same order as the two passes; measured
-// 2 % slower than the separate passes, so not the default.
-template <int TPW, bool XL>
-__device__ __forceinline__ void coupling_epilogue_err(DevParamsK& __restrict__ p, const Slot& ws,
-                                                      const float* __restrict__ Xs, const float* __restrict__ xown,
-                                                      const floatx16 (&acc)[TPW], bool pulse_on) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float knq[8], h[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        knq[q] = s_kn[mfma_env(q, lane)];
-        h[q] = s_ctl[mfma_env(q, lane)].h;
-    }
-    float part[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int t = 0; t < TPW; ++t) {
-        float w[8], u[8];
-        load8(ws, SL_W, t, w);
-        if (pulse_on) {
-            load8(ws, SL_P, t, u);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) u[q] = 0.0f;  // still added: x + 0 is not folded (signed zeros)
-        }
-        float y0[8], y1[8], f0[8], f2[8], f3[8], f4[8], f5[8];
-        load8(ws, SL_Y0, t, y0);
-        load8(ws, SL_Y1, t, y1);
-        load8(ws, SL_F0 + 0, t, f0);
-        load8(ws, SL_F0 + 2, t, f2);
-        load8(ws, SL_F0 + 3, t, f3);
-        load8(ws, SL_F0 + 4, t, f4);
-        load8(ws, SL_F0 + 5, t, f5);
-        const int i = 32 * (wave * TPW + t) + (lane & 31);
-        float f[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int e = mfma_env(q, lane);
-            const float P = acc[t][q], Q = acc[t][q + 8];
-            float sn, cs;
-            if constexpr (XL) {
-                sn = xown[xs_idx(e, i)];
-                cs = xown[xs_idx(16 + e, i)];
-            } else {
-                sn = Xs[xs_idx(e, i)];
-                cs = Xs[xs_idx(16 + e, i)];
-            }
-            const float tq = sn * Q;
-            const float coup = __builtin_fmaf(cs, P, -tq);
-            f[q] = __builtin_fmaf(knq[q], coup, w[q]) + u[q];
-        }
-        store8(ws, SL_F0 + 6, t, f);
-        err_dense_tile(p, ws, t, h, y0, y1, f0, f2, f3, f4, f5, f, part);
-    }
-    rm_publish(part, 0);
-}
-
 // After the 7th stage: error norm, accept/reject, dense-output saves with
 // LFP, FSAL -- for all 16 envs, every wave on its own columns.
 // One pass of post_step's saves: rounds r0 .. r0+nk-1 (nk = min(RCX, nrounds - r0))
@@ -1872,30 +1585,6 @@ __device__ __forceinline__ void save_rounds_setup(const CtlE& c, int e, int r0) 
         s_theta[e][k] = th;
         s_rflag[e][k] = fl;
     }
-}
-
-// Two save rounds at once on packed FP32 (v_pk_mul_f32 / v_pk_add_f32 /
-// v_pk_fma_f32 do two IEEE operations per instruction at the non-packed
-// instruction rate): kdm_cosf's cosine of both components, the same
-// operations in the same order as kdm_sincosf's c output (kura_detmath.h);
-// only the quadrant select stays per component.
-__device__ __forceinline__ kf2 kdm_cosf2(kf2 x) {
-    const kf2 j = __builtin_elementwise_rint(x * KDM_TWO_OVER_PI_F);
-    kf2 r = kf2_fma(-j, kf2(KDM_PIO2_C1), x);
-    r = kf2_fma(-j, kf2(KDM_PIO2_C2), r);
-    r = kf2_fma(-j, kf2(KDM_PIO2_C3), r);
-    const int q0 = ((int)j.x) & 3, q1 = ((int)j.y) & 3;
-    const kf2 z = r * r;
-    kf2 ps = kf2_fma(z, kf2(-1.9515295891e-4f), kf2(8.3321608736e-3f));
-    ps = kf2_fma(z, ps, kf2(-1.6666654611e-1f));
-    const kf2 sr = kf2_fma(r * z, ps, r);
-    kf2 pc = kf2_fma(z, kf2(2.443315711809948e-5f), kf2(-1.388731625493765e-3f));
-    pc = kf2_fma(z, pc, kf2(4.166664568298827e-2f));
-    const kf2 cr = kf2_fma(z * z, pc, kf2_fma(kf2(-0.5f), z, kf2(1.0f)));
-    float c0 = (q0 & 1) ? sr.x : cr.x, c1 = (q1 & 1) ? sr.y : cr.y;
-    c0 = ((q0 + 1) & 2) ? -c0 : c0;
-    c1 = ((q1 + 1) & 2) ? -c1 : c1;
-    return kf2{c0, c1};
 }
 
 template <int TPW, bool XL, int RCX, bool RS>
@@ -2094,79 +1783,11 @@ __device__ __forceinline__ void save_pass(DevParamsK& __restrict__ p, const Slot
             }
         }
     }
-#ifdef KURA_SAVE_PACKED
-    // A/B form (measured and dropped): naive LFP rounds k, k+1 of a (tile,
-    // env) evaluated as one packed pair (kdm_cosf2).  A round past nk has
-    // flags 0 (save_rounds_setup), so its half of a pair adds +0 to its
-    // partial and stores nothing; a partial is never -0 (it starts at +0), so
-    // p + 0 == p and the sums are those of the scalar loop below, bit for bit
-    // (GPU suite green on it).  The pairs double the solver's scratch (436 ->
-    // 856 B per lane for <4, false, bf16x3>): same box, env0 step 3.02 ->
-    // 3.21-3.39 ms and reset 55 -> 83 ms (profiles/r06_save_packed_ab.txt).
-    constexpr bool kPk = !XL && (RCX % 2 == 0);
-#else
-    constexpr bool kPk = false;
-#endif
+    // K1 / K2: tile by tile, one round at a time (rounds evaluated as packed
+    // FP32 pairs doubled the solver's scratch: step -6 to -11 %, reset +51 %,
+    // profiles/r06_save_packed_ab.txt)
 #pragma unroll 1
-    for (int t = 0; t < (kPk && !gauss && eval_rows ? TPW : 0); ++t) {
-        const int i = 32 * (wave * TPW + t) + (lane & 31);
-        float ca[8], cb[8], cc[8], f0[8], y0[8];
-        load8(ws, SL_CA, t, ca);
-        load8(ws, SL_CB, t, cb);
-        load8(ws, SL_CC, t, cc);
-        load8(ws, SL_F0, t, f0);
-        load8(ws, SL_Y0, t, y0);
-#ifdef KURA_STAMPS
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // attribute the record-load wait (diagnostic build)
-        STAMP(12);
-#endif
-        float k0[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) k0[q] = h[q] * f0[q];
-#pragma unroll
-        for (int k = 0; k < RCX; k += 2) {
-            if (k >= nk) break;  // wave-uniform: past every env's last save of this step
-            float v[2][8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const kf2 x = {th[k][q], th[k + 1][q]};
-                kf2 w = kf2(ca[q]) * x + kf2(cb[q]);
-                w = w * x + kf2(cc[q]);
-                w = w * x + kf2(k0[q]);
-                w = w * x + kf2(y0[q]);
-                v[0][q] = w.x;
-                v[1][q] = w.y;
-                const kf2 cr = kdm_cosf2(w);
-                const int f = fl[q] >> (3 * k);
-                const kf2 add = {(f & 2) ? cr.x : 0.0f, (f & 020) ? cr.y : 0.0f};
-                const kf2 s = kf2{pn[k][q], pn[k + 1][q]} + add;
-                pn[k][q] = s.x;
-                pn[k + 1][q] = s.y;
-            }
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                if ((fin >> (k + kk)) & 1) {  // the solve's last row: the new state
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int off = (mfma_env(q, lane) * NG + col0 + i) * 4;
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[kk][q]), ys,
-                                                              ((fl[q] >> (3 * (k + kk))) & 4) ? off : kDrop, 0, 0);
-                    }
-                }
-                if (capture) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int off = ((mfma_env(q, lane) * crow + rbase[q] + k + kk) * NG + col0 + i) * 4;
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[kk][q]), rws,
-                                                              ((fl[q] >> (3 * (k + kk))) & 1) ? off : kDrop, 0, 0);
-                    }
-                }
-            }
-        }
-        STAMP(13);
-    }
-#pragma unroll 1
-    for (int t = 0; t < (!XL && !(kPk && !gauss) && eval_rows ? TPW : 0); ++t) {
+    for (int t = 0; t < (!XL && eval_rows ? TPW : 0); ++t) {
         const int i = 32 * (wave * TPW + t) + (lane & 31);
         float ca[8], cb[8], cc[8], f0[8], y0[8];
         double G[8];
@@ -2320,12 +1941,11 @@ __device__ __forceinline__ int post_step(DevParamsK& __restrict__ p, Slot& ws, i
     float h[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) h[q] = s_ctl[mfma_env(q, lane)].h;
-#ifndef KURA_FUSED_ERR
     // (1) scaled error partials and dense-output coefficients: a pass of its
-    // own.  (-DKURA_FUSED_ERR folds it into the stage-6 epilogue instead:
-    // one record round trip and one barrier less per Dopri step, yet 2 %
-    // slower in the same-box A/B -- the fused epilogue holds the
-    // accumulators and the seven records of a tile at once)
+    // own.  (Folded into the stage-6 epilogue it saves one record round trip
+    // and one barrier per Dopri step, yet was 2 % slower in the same-box A/B:
+    // the fused epilogue holds the accumulators and the seven records of a
+    // tile at once)
     float part[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // (kept rolled: the unrolled loop measured 0.4 % slower, same box,
     // profiles/r04_solver_ab.txt)
@@ -2345,9 +1965,6 @@ __device__ __forceinline__ int post_step(DevParamsK& __restrict__ p, Slot& ws, i
     rm_publish(part, 0);
     STAMP(5);
     lds_barrier();
-#endif
-    // (KURA_FUSED_ERR: the scaled error partials of every wave are in
-    // s_red[0], behind the stage-6 epilogue's barrier)
     float etot[1] = {tid < E_WG ? rm_total(tid, 0) : 0.0f};
     if constexpr (XL) {
         double dummy[1] = {0.0};
@@ -2473,18 +2090,13 @@ __device__ __forceinline__ int post_step(DevParamsK& __restrict__ p, Slot& ws, i
 // One diffeqsolve for the workgroup's 16 envs.  s_ctl must be initialised
 // (ctl_begin) and visible before the call.
 // The solver is a called function (one call site per kernel; its frame saves
-// the callee-saved registers once per solve).  Inlined (-DKURA_SOLVE_INLINE)
-// the kernel needs less scratch (648 vs ~1200 B per lane for <4, false>) but
-// the register allocation of the combined body spills inside the sweep loop:
-// same-box A/B, 0.750 vs 0.788 of the FP32 MFMA peak.
-#ifdef KURA_SOLVE_INLINE
-#define KURA_SOLVE_ATTR __forceinline__
-#else
-#define KURA_SOLVE_ATTR __noinline__
-#endif
+// the callee-saved registers once per solve).  Inlined the kernel needs less
+// scratch (648 vs ~1200 B per lane for <4, false>) but the register
+// allocation of the combined body spills inside the sweep loop: same-box A/B,
+// 0.750 vs 0.788 of the FP32 MFMA peak.
 template <int TPW, bool XL, bool SP, bool RS>
-__device__ KURA_SOLVE_ATTR void solve_wg(DevParamsK& __restrict__ pin, float* Xs, int env_base, bool pulse_on,
-                         long long* rhs_count, Part& pt) {
+__device__ __noinline__ void solve_wg(DevParamsK& __restrict__ pin, float* Xs, int env_base, bool pulse_on,
+                                      long long* rhs_count, Part& pt) {
     // (the kernarg segment through the VGPR-passed pointer: vector loads.
     // Made wave-uniform -- scalar loads, which share lgkmcnt with the LDS
     // traffic -- the step was 1.5 % slower in the same-box A/B,
@@ -2528,11 +2140,7 @@ __device__ KURA_SOLVE_ATTR void solve_wg(DevParamsK& __restrict__ pin, float* Xs
     STAMP(0);
     for (;;) {
         floatx16 acc[TPW];
-#ifdef KURA_EXP_NO_B1   // measurement-only upper bound (races: results invalid)
-        if (XL || s == 0 || s == 1) lds_barrier();
-#else
         lds_barrier();
-#endif
         STAMP(1);
         const float* xown = nullptr;
         if constexpr (XL) {
@@ -2565,26 +2173,16 @@ __device__ KURA_SOLVE_ATTR void solve_wg(DevParamsK& __restrict__ pin, float* Xs
                           (lane & 31)] = acc[t][q];
             }
 #else
-#if KURA_RESET_DEDUP
-            if constexpr (SP && RS)
+            if constexpr (SP && RS)   // the reset reads the deduplicated image
                 coupling_gemm_bf16x3_dd<TPW>(Xs, p.alpha_dd, p.alpha_dd_bytes, acc);
             else
-#endif
                 coupling_gemm<TPW, SP>(Xs, p.alpha_sw, p.alpha_reuse, acc);
 #endif
         }
         STAMP(2);
-#ifdef KURA_FUSED_ERR
-        if (s == 6) coupling_epilogue_err<TPW, XL>(p, ws, Xs, xown, acc, pulse_on);
-        else
-#endif
-            coupling_epilogue<TPW, XL>(p, ws, Xs, xown, acc, s, pulse_on);
+        coupling_epilogue<TPW, XL>(p, ws, Xs, xown, acc, s, pulse_on);
         STAMP(3);
-#ifdef KURA_EXP_NO_B2   // measurement-only upper bound (races: results invalid)
-        if (XL || s == 0 || s == 6) lds_barrier();
-#else
         lds_barrier();  // every wave is done reading the operand before it is rewritten
-#endif
         STAMP(4);
         ++nrhs;
         if (s > 0 && s < 6) {

@@ -95,6 +95,36 @@ int main(void) {
             assert getattr(abi.KuraConfig, f).offset == int(off), f
 
 
+# Build switches of settled experiments ("Retired build
+# switches"): their code is deleted, and a command line that still passes one
+# must fail instead of building the product under a variant's name.
+RETIRED_SWITCHES = ["KURA_EXP_ALPHA", "KURA_EXP_ORDER", "KURA_EXP_NO_B1", "KURA_EXP_NO_B2", "KURA_SPLIT_SCALAR",
+                    "KURA_SI_PACKED", "KURA_GROUPSUM_ATOMIC", "KURA_FUSED_ERR", "KURA_SAVE_PACKED",
+                    "KURA_SOLVE_INLINE", "KURA_RESET_DEDUP", "KURA_REC_LD_AUX", "KURA_REC_ST_AUX", "KURA_BITSEL"]
+
+
+def _preprocess_kernels(*defines):
+    import __graft_entry__ as ge
+    if not os.path.exists(ge.HIPCC):
+        pytest.skip("no hipcc")
+    return subprocess.run([ge.HIPCC, *ge.HIP_FLAGS, *defines, "-E", "-o", os.devnull,
+                           os.path.join(ge.CSRC, "kura_kernels.hip")], capture_output=True, text=True)
+
+
+def test_kernel_source_preprocesses_plain():
+    r = _preprocess_kernels()
+    assert r.returncode == 0, r.stderr
+
+
+@pytest.mark.parametrize("macro", RETIRED_SWITCHES)
+def test_retired_build_switch_is_an_error(macro):
+    r = _preprocess_kernels(f"-D{macro}=1")
+    assert r.returncode != 0
+    # the #error's own text, not just the echoed command line
+    msg = [ln for ln in r.stderr.splitlines() if "error:" in ln and "retired build switch" in ln]
+    assert msg and macro in msg[0], r.stderr
+
+
 def test_metric_entry_points_reject_null_handle():
     """Argument checks run before any HIP call: a null handle is
     KURA_E_INVALID (-1) for the episode-metric entry points, no GPU needed."""
